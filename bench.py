@@ -19,6 +19,13 @@ c4-up (C4 + one weak edge to its own round: the general sweep serves every query
 takes such an edge at this size, the general sweep's parity is tests/test_gpu_irregular.py's),
 --deliver paper (dedup across pops).
 
+A plain run (--gpus 1 --steps N --warmup W) sets up, warms up, times the N steps and
+prints the line.  --full adds what takes runs of its own: the profiling replay behind
+the per-kernel and roofline figures, and the CPU baselines with the check of the GPU's
+outputs against the bitset oracle (--no-cpu drops those two again).  --dump-outputs DIR
+writes the last timed step's outputs as DIR/<name>.npy (dump_outputs); the inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
+
 --gpus N without torchrun: spawns N ranks (torch.distributed.run) before anything
 touches a GPU; under torchrun WORLD_SIZE must equal N.  For C4 at N > 1 the line
 is BASELINE.json configs[3] as named: ONE C4 DAG (seed 4) with its process columns
@@ -274,6 +281,48 @@ def same_replay(a, b) -> bool:
                                                                          b.deliver_edges))
 
 
+DUMP_CAP_BYTES = 60 * 1000 * 1000  # --dump-outputs: every file together stays below 64 MB
+
+
+def replay_arrays(res) -> dict:
+    """A replay's outputs as named arrays (what a caller of dr_replay receives); res: one
+    ReplayResult, or a list of them (C5: the DAGs' outputs one after another)."""
+    import numpy as np
+
+    rs = res if isinstance(res, (list, tuple)) else [res]
+    out = {k: np.concatenate([np.asarray(getattr(r, k)) for r in rs])
+           for k in ("commit", "vcount", "push_off", "push_wave", "pop_count", "pop_digest", "pop_edges")}
+    out["edge_totals"] = np.asarray([[r.commit_edges, r.chain_edges, r.deliver_edges] for r in rs], np.uint64)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: write each array as path/<name>.npy in float64.  pop_digest uses
+    all 64 bits, which a double cannot hold: it goes out as two files, pop_digest_hi and
+    pop_digest_lo, its upper and lower 32 bits.  Every other integer must be below 2^53
+    (exact in a double).  An output too large for its share of DUMP_CAP_BYTES is sampled
+    at fixed, seeded positions."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if name == "pop_digest":
+            u = a.view(np.uint64)
+            files[name + "_hi"], files[name + "_lo"] = u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)
+        else:
+            if a.size and int(np.abs(a).max()) >= 1 << 53:
+                raise ValueError(f"--dump-outputs: {name} does not fit a double exactly")
+            files[name] = a
+    cap = DUMP_CAP_BYTES // 8 // max(len(files), 1)  # float64 elements per file
+    for name, a in files.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def kernel_bytes(cfg, d, res, dreg=None, mstat=None, wu_fused=True):
     """Algorithmic bytes per launch of each replay phase.  dreg: the engine's
     regular weak window (the summaries' depth; deeper weak edges are exceptions, s3.5).
@@ -302,6 +351,29 @@ def kernel_bytes(cfg, d, res, dreg=None, mstat=None, wu_fused=True):
                       bytes=sw["row_bytes"] + sw["weak_scanned"] * (W * 8 + 4) + sw["shortcut"] * (1 + dd) * W * 8
                       + (sw["partial"] + sw["shortcut"]) * 3 * W * 8),
     }
+
+
+def roofline_of(args, cfg, d, res, exc, mstat):
+    """--full: the line's roofline entry and detail.kernels from the profiled phase times
+    (res.ms) and kernel_bytes."""
+    kb = kernel_bytes(cfg, d, res, exc["regular_delta"], mstat, (fuse_mask() & 1) != 0)
+    # dominant kernel = the phase with the largest device time (HIP events)
+    dom = max(kb, key=lambda k: kb[k]["ms"])
+    ach = kb[dom]["bytes"] / (kb[dom]["ms"] / 1e3) / 1e9 if kb[dom]["ms"] > 0 else 0.0
+    # PMC traffic of the dominant phase's kernels for this row stride (REF delivery: the
+    # profiled launch sequence); lines whose dominant kernel moves < 1 % of peak in its time
+    # are latency-bound and say so
+    tr_bytes, tr_file = (measured_traffic(dom, (cfg.n + 63) // 64, cfg.name)
+                         if args.deliver == "ref" and not args.no_memo else (None, None))
+    bound = "hbm" if ach >= 0.01 * HBM_PEAK_GBS else "latency"
+    roofline = {"bound": bound, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS,
+                "traffic": tr_bytes, "traffic_unit": f"bytes/launch (rocprofv3 PMC, {tr_file})",
+                "kernel": kb[dom]["kernel"], "bytes_per_launch": kb[dom]["bytes"],
+                "ms_per_launch": kb[dom]["ms"]}
+    kernels = {k: dict(v, GBps=(v["bytes"] / (v["ms"] / 1e3) / 1e9 if v["ms"] > 0 else None))
+               for k, v in kb.items()}
+    return roofline, kernels
 
 
 def weak_columns(d):
@@ -448,6 +520,8 @@ def run_rank_share(args, local: int):
     cm = np.concatenate([np.asarray(s["commit"], np.uint8) for s in shares])
     vc = np.concatenate([np.asarray(s["vcount"], np.int32) for s in shares])
     ok = bool((cm == fc).all() and (vc == fv).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(commit=cm, vcount=vc))
     slow = max(shares, key=lambda s: s["ms"])
     # commit edges of the slowest share: strong degrees of rounds 4w-2..4w of its waves
     deg = np.asarray([int(np.unpackbits(d.strong[r * cfg.n * d.W:(r + 1) * cfg.n * d.W].view(np.uint8)).sum())
@@ -553,6 +627,8 @@ def run_wave_split_shares(args, local: int):
         e.append_packed(d)
         want = e.replay(cfg.nwaves, L.DR_CHAIN_PERSISTENT, L.DR_DELIVER_REF)
     ok = same_replay(got, want)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, replay_arrays(got))
     slow = max(shares, key=lambda x: x["ms"])
     # the slowest share's edges: its owned commits, chains and pops
     k = slow["rank"]
@@ -853,8 +929,10 @@ def run_c5(args, rank: int, world: int, local: int, dist):
     dt, total_edges = reduce_over_ranks(dist, wall, edges, "cuda")
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, replay_arrays(res))
     cpu = None
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         cpu = cpu_c5(dags, args.deliver_mode, res) if not args.dags else None
     ach = dag_bytes / (kms / 1e3) / 1e9 if kms > 0 else 0.0
     form = b.form()  # the fused kernel that ran (AUTO: the wave form above 6 DAGs per CU)
@@ -1004,6 +1082,10 @@ def run_loop(args, local: int):
         ref = e.replay(nw, L.DR_CHAIN_PERSISTENT, L.DR_DELIVER_REF)
     ok = bool((cm == ref.commit).all() and (vc == ref.vcount).all() and pushes == ref.push_wave.tolist()
               and pc == ref.pop_count.tolist() and pdg == ref.pop_digest.tolist())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(commit=cm, vcount=vc, push_wave=np.asarray(pushes, np.int32),
+                                             pop_count=np.asarray(pc, np.uint64),
+                                             pop_digest=np.asarray(pdg, np.uint64)))
 
     def pct(x):
         a = np.asarray(x) * 1e6
@@ -1087,6 +1169,12 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the profiling replay (per-kernel and "
+                         "roofline figures) and the CPU baselines with the check against the bitset oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64; the 64-bit pop digests as "
+                         "pop_digest_hi / pop_digest_lo)")
     ap.add_argument("--config", default="c4", choices=["c1", "c2", "c3", "c4", "c4-deep", "c4-deep64", "c4-dups", "c5",
                                                        "c4-loop", "c4-far", "c4-q8", "c4-up"])
     ap.add_argument("--graph", action="store_true",
@@ -1223,13 +1311,18 @@ def main() -> int:
                                       ("commit", "vcount", "push_off", "push_wave", "pop_count", "pop_digest",
                                        "pop_edges")})
     dt, total_edges = reduce_over_ranks(dist, wall, res.total_edges, "cuda")
-    eng.set_phase_timing(2)
-    prof = eng.replay(cfg.nwaves, L.DR_CHAIN_PERSISTENT, args.deliver_mode)  # per-phase HIP event times
-    res.ms = dict(prof.ms, summary=ms_summary / max(n_ev, 1))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, replay_arrays(res))
+    if args.full:
+        eng.set_phase_timing(2)
+        prof = eng.replay(cfg.nwaves, L.DR_CHAIN_PERSISTENT, args.deliver_mode)  # per-phase HIP event times
+        res.ms = dict(prof.ms, summary=ms_summary / max(n_ev, 1))
+    else:  # the timed steps' own events: the summary pass only
+        res.ms = dict(summary=ms_summary / max(n_ev, 1))
 
     verify = None
     cpu = cpu2 = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         runs = 5 if cfg.n * cfg.last_round <= 1024 * 4000 else 3
         cpu2, want = cpu_bitset(cfg, d, CPU_THREADS, runs, args.deliver_mode)
         verify = same_replay(res, want)
@@ -1287,16 +1380,9 @@ def main() -> int:
         return 0
 
     exc = eng.exception_stats()
-    kb = kernel_bytes(cfg, d, res, exc["regular_delta"], eng.mirror_stats(), (fuse_mask() & 1) != 0)
-    # dominant kernel = the phase with the largest device time (HIP events)
-    dom = max(kb, key=lambda k: kb[k]["ms"])
-    ach = kb[dom]["bytes"] / (kb[dom]["ms"] / 1e3) / 1e9 if kb[dom]["ms"] > 0 else 0.0
-    # PMC traffic of the dominant phase's kernels for this row stride (REF delivery: the
-    # profiled launch sequence); lines whose dominant kernel moves < 1 % of peak in its time
-    # are latency-bound and say so
-    tr_bytes, tr_file = (measured_traffic(dom, (cfg.n + 63) // 64, cfg.name) if args.deliver == "ref" and not args.no_memo
-                         else (None, None))
-    bound = "hbm" if ach >= 0.01 * HBM_PEAK_GBS else "latency"
+    roofline = kernels = None
+    if args.full:  # the per-phase times come from the profiling replay
+        roofline, kernels = roofline_of(args, cfg, d, res, exc, eng.mirror_stats())
     ms_per_step = dt / args.steps * 1e3
     out = {
         "metric": "DAG edges traversed/sec (commit+delivery)",
@@ -1318,26 +1404,21 @@ def main() -> int:
                                + (" -- memo off (DR_OPT_MEMO 0): every cone swept whole" if args.no_memo else ""),
                    "n": cfg.n, "rounds": cfg.last_round, "waves": cfg.nwaves,
                    "parallelism": f"replicas{world}" if world > 1 else "single"},
-        "roofline": {"bound": bound, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": ach / HBM_PEAK_GBS,
-                     "traffic": tr_bytes, "traffic_unit": f"bytes/launch (rocprofv3 PMC, {tr_file})",
-                     "kernel": kb[dom]["kernel"], "bytes_per_launch": kb[dom]["bytes"],
-                     "ms_per_launch": kb[dom]["ms"]},
+        "roofline": roofline,
         "cpu_baseline": cpu,
         "cpu_bitset": cpu2,
         "detail": {"edges_per_step": res.total_edges, "commit_edges": res.commit_edges,
                    "chain_edges": res.chain_edges, "deliver_edges": res.deliver_edges,
                    "commits": int(res.commit.sum()), "pops": int(len(res.pop_count)),
                    "ms": res.ms, "ms_note": f"summary: mean over the {n_ev} timed steps whose summary pass HIP events "
-                   f"bracket (every {every}th: each record costs the stream ~4 us); other phases: one "
+                   f"bracket (every {every}th: each record costs the stream ~4 us); other phases (--full): one "
                    "profiling replay after them (DR_OPT_PHASE_TIMING=2)",
                    "sweep": res.sweep, "verify_vs_oracle": verify, "exceptions": exc,
                    "replay_path": {0: "memo", 1: "memo, upward weak edges verified (k_verify_up)",
                                    2: "general sweep (an upward edge changes a cone)", 3: "general sweep",
                                    -1: "none"}.get(eng.last_replay_path(), "?"),
                    "commit_split": split, "colshard": colshard[0] if colshard else None,
-                   "kernels": {k: dict(v, GBps=(v["bytes"] / (v["ms"] / 1e3) / 1e9 if v["ms"] > 0 else None))
-                               for k, v in kb.items()}},
+                   "kernels": kernels},
     }
     if multi:
         out = c4_multi_line(args, world, colshard, dict(value=out["value"], ms_per_step=ms_per_step,

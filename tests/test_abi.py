@@ -1,6 +1,5 @@
 """CPU checks of the drop-in boundary: the C-ABI library loads, exports every symbol
 declared in include/*.h, and refuses to run without a GPU (no CPU fallback)."""
-import ctypes
 import os
 import re
 import subprocess
@@ -48,21 +47,32 @@ def test_library_loads_and_binds():
     assert L.dr_abi_version() == 2
 
 
-def test_no_cpu_fallback():
-    L = _lib.lib()
-    h = ctypes.c_void_p()
-    if os.environ.get("HIP_VISIBLE_DEVICES") is None:
-        try:
-            import torch
+_NO_DEVICE_CHILD = """
+import ctypes, json, sys
+sys.path.insert(0, sys.argv[1])
+from dag_rider_amd import _lib
+L = _lib.lib()
+h = ctypes.c_void_p()
+rc = L.dr_create(4, 1, 8, 0, ctypes.byref(h))
+err = L.dr_last_error(None).decode()
+print(json.dumps(dict(rc=rc, err=err, rc_neg=L.dr_create(4, 1, 8, -1, ctypes.byref(h)))))
+"""
 
-            if torch.cuda.is_available():
-                pytest.skip("a GPU is visible")
-        except Exception:
-            pass
-    rc = L.dr_create(4, 1, 8, 0, ctypes.byref(h))
-    assert rc == _lib.DR_E_HIP
-    assert b"no CPU fallback" in L.dr_last_error(None)
-    assert L.dr_create(4, 1, 8, -1, ctypes.byref(h)) == _lib.DR_E_INVAL
+
+def test_no_cpu_fallback():
+    """In a fresh process that sees no HIP device (HIP_VISIBLE_DEVICES=-1 hides every
+    device of a machine that has some), dr_create refuses instead of falling back."""
+    import json
+    import sys
+
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
+    p = subprocess.run([sys.executable, "-c", _NO_DEVICE_CHILD, ROOT], capture_output=True, text=True, timeout=120,
+                       env=env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])
+    assert out["rc"] == _lib.DR_E_HIP
+    assert "no CPU fallback" in out["err"]
+    assert out["rc_neg"] == _lib.DR_E_INVAL
 
 
 def test_oracle_not_linked_by_product():

@@ -17,7 +17,7 @@ for f in glob.glob(os.path.join(d, "**", "*memory_copy_trace.csv"), recursive=Tr
     for r in csv.DictReader(open(f)):
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "C " + r.get("Direction", "") + " " + r.get("Size", r.get("Bytes", ""))))
 ev.sort()
-# bench.py's last replay is a profiling one (every phase bracketed by HIP events);
+# bench.py --full's last replay is a profiling one (every phase bracketed by HIP events);
 # the last TIMED step starts at the second-to-last k_summary_commit (--last: the last)
 mark = sys.argv[sys.argv.index("--start") + 1] if "--start" in sys.argv else "k_summary_commit"
 starts = [i for i, e in enumerate(ev) if mark in e[2]]
