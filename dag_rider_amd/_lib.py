@@ -27,6 +27,7 @@ DR_OPT_COMMIT_SPLIT = 5
 DR_OPT_REPLAY_GRAPH = 6
 DR_OPT_FUSE = 7
 DR_OPT_CALL_OVERLAP = 8
+DR_OPT_DEVICE_IDS = 9
 DR_CREATE_SHARED_STREAM = 1
 DR_BATCH_AUTO, DR_BATCH_WORKGROUP, DR_BATCH_WAVE = 0, 1, 2
 DR_LEADER_CONST1, DR_LEADER_SEEDED, DR_LEADER_TABLE = 0, 1, 2
@@ -109,6 +110,7 @@ SIGNATURES = {
     "dr_last_append_phases": (C.c_int, [P, C.POINTER(f32)]),
     "dr_set_slice": (C.c_int, [P, C.POINTER(SliceCfg)]),
     "dr_last_replay_path": (C.c_int, [P]),
+    "dr_last_ids_form": (C.c_int, [P]),
     "dr_slice_result": (C.c_int, [P, C.POINTER(SliceOut)]),
     # include/dagrider_shard.h
     "dr_shard_unique_id": (C.c_int, [P]),

@@ -273,6 +273,8 @@ struct dr_ctx {
   std::vector<uint64_t> last_key, rg_key;
   hipGraphExec_t rg_exec = nullptr;
   int plan_mode = 1;        // DR_OPT_DEVICE_PLAN: dr_replay planned on the device when it applies
+  int device_ids = 1;       // DR_OPT_DEVICE_IDS: a PAPER dr_replay that requests ids stays device-planned
+  int ids_form = -1;        // dr_last_ids_form
   int batch_form = DR_BATCH_AUTO;  // DR_OPT_BATCH_FORM (dr_replay_batch, first context)
   int last_batch_form = 0;         // dr_last_batch_form: the fused form this context's last batch ran
   float append_phases[4] = {};     // dr_last_append_phases: the last dr_append_rounds_packed (host ms)
@@ -2317,6 +2319,10 @@ extern "C" int dr_set_option(dr_ctx *c, int option, int value) {
     c->plan_mode = value != 0;
     return DR_OK;
   }
+  if (option == DR_OPT_DEVICE_IDS) {
+    c->device_ids = value != 0;
+    return DR_OK;
+  }
   if (option == DR_OPT_COMMIT_SPLIT) {
     if (value < 0 || value > 2) return c->fail(DR_E_INVAL, "DR_OPT_COMMIT_SPLIT is 0, 1 or 2");
     c->commit_split = value;
@@ -3465,21 +3471,57 @@ template <int WS>
 hipError_t launch_paper_emit_t(dr_ctx *c, int nw, const int32_t *plan, const dr::SweepQuery *dq,
                                const int32_t *firstpop, const int32_t *qcut, const int32_t *qlo,
                                const uint32_t *firstK, const uint32_t *qr_off, const int32_t *qr_list, u64 *qcount,
-                               u64 *qdigest, u64 *qedges) {
-  hipLaunchKernelGGL((dr::k_paper_emit<WS, 512>), dim3(nw), dim3(512), 0, c->stream, c->view(), c->K.as<u64>(),
-                     c->masks.as<u64>(), plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list,
-                     c->slot_off.as<uint32_t>(), c->slot_src.as<uint16_t>(), qcount, qdigest, qedges);
+                               u64 *qdigest, u64 *qedges, const dr::PaperIds *pid) {
+  if (pid)  // ids requested: the rounds' positions kept for k_paper_ids
+    hipLaunchKernelGGL((dr::k_paper_emit<WS, 512, true>), dim3(nw), dim3(512), 0, c->stream, c->view(),
+                       c->K.as<u64>(), c->masks.as<u64>(), plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list,
+                       c->slot_off.as<uint32_t>(), c->slot_src.as<uint16_t>(), qcount, qdigest, qedges, *pid);
+  else
+    hipLaunchKernelGGL((dr::k_paper_emit<WS, 512, false>), dim3(nw), dim3(512), 0, c->stream, c->view(),
+                       c->K.as<u64>(), c->masks.as<u64>(), plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list,
+                       c->slot_off.as<uint32_t>(), c->slot_src.as<uint16_t>(), qcount, qdigest, qedges,
+                       dr::PaperIds{});
   return hipGetLastError();
 }
 hipError_t launch_paper_emit(dr_ctx *c, int nw, const int32_t *plan, const dr::SweepQuery *dq,
                              const int32_t *firstpop, const int32_t *qcut, const int32_t *qlo, const uint32_t *firstK,
                              const uint32_t *qr_off, const int32_t *qr_list, u64 *qcount, u64 *qdigest,
-                             u64 *qedges) {
+                             u64 *qedges, const dr::PaperIds *pid) {
   switch (c->WS) {
 #define DR_PE(W) \
-  case W: return launch_paper_emit_t<W>(c, nw, plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list, qcount, qdigest, qedges);
+  case W: return launch_paper_emit_t<W>(c, nw, plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list, qcount, qdigest, qedges, pid);
     DR_PE(1) DR_PE(2) DR_PE(4) DR_PE(8) DR_PE(16) DR_PE(32)
 #undef DR_PE
+  }
+  return hipErrorInvalidValue;
+}
+
+// The PAPER id pass (replay_plan.hpp): a wave per round, four rounds an item, so C4's ~4000
+// delivered rounds make ~1000 items of 256 threads, about four workgroups a CU; the kernel
+// holds no LDS and its waves never wait for each other.  The item count is known on the
+// device only, so the grid is fixed (8 workgroups a CU of an MI355X) and strides over the
+// items.  Measured at C4: 45 us for 32.7 MB of ids.
+constexpr int kPaperIdsNT = 256;
+template <int WS>
+hipError_t launch_paper_ids_t(dr_ctx *c, const int32_t *plan, const dr::SweepQuery *dq, const int32_t *firstpop,
+                              const int32_t *qcut, const uint32_t *firstK, const uint32_t *qr_off,
+                              const int32_t *qr_list, const dr::PaperIds &pid, const int64_t *qpos,
+                              const int32_t *item_pref, int64_t ids_cap) {
+  hipLaunchKernelGGL((dr::k_paper_ids<WS, kPaperIdsNT>), dim3(2048), dim3(kPaperIdsNT), 0, c->stream, c->view(),
+                     c->K.as<u64>(), c->masks.as<u64>(), plan, dq, firstpop, qcut, firstK, qr_off, qr_list,
+                     c->slot_off.as<uint32_t>(), c->slot_src.as<uint16_t>(), pid, qpos, item_pref, c->ids.as<int2>(),
+                     ids_cap);
+  return hipGetLastError();
+}
+hipError_t launch_paper_ids(dr_ctx *c, const int32_t *plan, const dr::SweepQuery *dq, const int32_t *firstpop,
+                            const int32_t *qcut, const uint32_t *firstK, const uint32_t *qr_off,
+                            const int32_t *qr_list, const dr::PaperIds &pid, const int64_t *qpos,
+                            const int32_t *item_pref, int64_t ids_cap) {
+  switch (c->WS) {
+#define DR_PI(W) \
+  case W: return launch_paper_ids_t<W>(c, plan, dq, firstpop, qcut, firstK, qr_off, qr_list, pid, qpos, item_pref, ids_cap);
+    DR_PI(1) DR_PI(2) DR_PI(4) DR_PI(8) DR_PI(16) DR_PI(32)
+#undef DR_PI
   }
   return hipErrorInvalidValue;
 }
@@ -3760,8 +3802,12 @@ hipError_t launch_verify_up(dr_ctx *c, const int32_t *stops, const int32_t *qcut
   return hipErrorInvalidValue;
 }
 
-int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out *o) {
+int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out *o, bool want_ids = false) {
   const int WS = c->WS, T = c->nrounds - 1;
+  // PAPER ids (DR_OPT_DEVICE_IDS): the id pass after the final pass writes the total order into
+  // the context's id buffer.  Such a replay launches kernel by kernel: the id buffers are no
+  // part of graph_key.
+  const bool graph_ok = !want_ids && c->replay_graph && !c->graph_fail && c->phase_timing <= 1 && !c->shared_stream;
   const bool persistent = chain_mode == DR_CHAIN_PERSISTENT;
   const int64_t pbound = persistent ? 2 * (int64_t)nw + 1 : (int64_t)nw * (nw + 1) / 2;
   const int64_t pcap = std::max<int64_t>(1, std::min<int64_t>(o->push_cap, pbound));
@@ -3772,7 +3818,7 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
   // A replay that launches kernel by kernel starts the row pass first: the host's planning
   // below (arena, static query table, launch arguments) then runs beside it instead of
   // before it (the row pass needs only the summary buffers and the commit flags)
-  const bool early = !(c->replay_graph && !c->graph_fail && c->phase_timing <= 1 && !c->shared_stream);
+  const bool early = !graph_ok;
   if (early) {
     HIPCHK(c, c->commit.ensure((size_t)std::max(nw, 1)));
     HIPCHK(c, c->vcount.ensure((size_t)std::max(nw, 1) * 4));
@@ -3789,6 +3835,9 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
   u64 *cedges, *cwedges, *dedges, *dwedges, *dstats, *qcount, *qdigest, *qedges = nullptr;
   int32_t *cstops, *qcut, *firstpop = nullptr, *qlo = nullptr, *qr_list = nullptr;
   uint32_t *firstK = nullptr, *qr_cnt = nullptr, *qr_off = nullptr;
+  dr::PaperIds pid{};
+  int64_t *qpos = nullptr;
+  int32_t *item_pref = nullptr;
   for (int pass = 0; pass < 2; pass++) {
     cv.off = 0;
     plan = cv.take<int32_t>(dr::PL_N);
@@ -3827,12 +3876,23 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
     pop_wave = cv.take<int32_t>(pcap);
     pop_cur = cv.take<int32_t>(pcap);
     pop_q = cv.take<int32_t>(pcap);
+    if (want_ids) {  // (last: the arena of a replay without ids is laid out as before)
+      pid.qa = cv.take<int32_t>(nw);
+      pid.pos_k = cv.take<uint32_t>((size_t)T + 2);
+      pid.pos_own = cv.take<uint32_t>(mask_words / WS);  // one per qr_list entry
+      qpos = cv.take<int64_t>(nw);
+      item_pref = cv.take<int32_t>((size_t)nw + 1);
+    }
     if (pass == 0) {
       HIPCHK(c, c->plan_arena.ensure(cv.off));
       cv.base = static_cast<char *>(c->plan_arena.p);
     }
   }
   HIPCHK(c, c->masks.ensure(mask_words * 8));
+  // the id buffer, sized before any launch argument takes its pointer: a PAPER stream holds
+  // at most one id per mirrored slot
+  const int64_t ids_n = want_ids ? std::min<int64_t>(o->ids_cap, (int64_t)c->h_slot_off.back()) : 0;
+  if (want_ids) HIPCHK(c, c->ids.ensure((size_t)std::max<int64_t>(ids_n, 1) * 8));
   // outputs: the emitting sweep's final pass packs them into one device region, which comes back
   // in one copy (writing them straight into pinned host memory from the kernel
   // took 19.5 us, profiles/r02/v27_timeline.txt)
@@ -3859,7 +3919,7 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
   // launch sequence depends on changed since it was captured; capture when this
   // call's configuration matches the previous call's (every buffer is sized then)
   enum { EAGER, CAPTURE, LAUNCH } form = EAGER;
-  if (c->replay_graph && !c->graph_fail && c->phase_timing <= 1 && !c->shared_stream) {
+  if (graph_ok) {
     if (c->pin_used || !c->pend.empty() || !c->h2q.empty()) HIPCHK(c, c->sync());  // the stage starts at pin
     const std::vector<uint64_t> key = graph_key(c, nw, chain_mode, paper, pcap);
     if (c->rg_exec && key == c->rg_key)
@@ -4018,7 +4078,7 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
                          pop_q, dq, dstops, firstpop, qcut, qlo, firstK, qr_cnt, qr_off, qr_list);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, launch_paper_emit(c, nw, plan, dq, firstpop, qcut, qlo, firstK, qr_off, qr_list, qcount, qdigest,
-                                  qedges));
+                                  qedges, want_ids ? &pid : nullptr));
       em.fin.firstpop = firstpop;
       em.fin.qedges = qedges;
     } else {  // REF: own rounds above the cut; workgroup 0 the canonical prefixes G, E, the last the pop plan
@@ -4037,6 +4097,14 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
     // 5. per-pop totals and outputs (the canonical prefixes came from the sweep launch's extra workgroup)
     hipLaunchKernelGGL((dr::k_replay_final<1024>), dim3(1), dim3(1024), 0, c->stream, em);
     HIPCHK(c, hipGetLastError());
+    if (want_ids) {  // 6. the PAPER order's ids: global positions and work items, then a wave per round
+      HIPCHK(c, c->rec(4));
+      hipLaunchKernelGGL((dr::k_paper_ids_plan<1024>), dim3(1), dim3(1024), 0, c->stream, plan, pop_q, dq, firstpop,
+                         pid.qa, qcount, kPaperIdsNT / 64, qpos, item_pref);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, launch_paper_ids(c, plan, dq, firstpop, qcut, firstK, qr_off, qr_list, pid, qpos, item_pref, ids_n));
+      HIPCHK(c, c->rec(5));
+    }
     if (stage) {  // graph: the outputs into pinned memory inside the graph
       const dr::CopySeg sg{c->plan_out.as<uint8_t>(), reinterpret_cast<uint8_t *>(stage), out_bytes};
       HIPCHK(c, c->launch_copies(&sg, 1));
@@ -4095,7 +4163,7 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
     HIPCHK(c, c->d2h(c->plan_host.data(), c->plan_out.p, out_bytes));
     HIPCHK(c, c->sync());
     hb = c->plan_host.data();
-    c->graph_state = c->graph_fail ? -1 : 0;
+    c->graph_state = c->graph_fail && !want_ids ? -1 : 0;  // (with ids: kernel by kernel by design)
   }
   c->last_key = graph_key(c, nw, chain_mode, paper, pcap);
   {  // device addresses -> the same offsets in the host copy
@@ -4144,6 +4212,17 @@ int replay_planned(dr_ctx *c, int nw, int chain_mode, bool paper, dr_replay_out 
   o->sweep_weak_scanned = h_hdr[dr::PH_WEAK];
   o->sweep_shortcut = h_hdr[dr::PH_SHORT];
   o->n_ids = 0;
+  if (want_ids) {  // every vertex is delivered once: the stream's length is the pops' counts added up
+    int64_t tot = 0;
+    for (int64_t p = 0; p < np; p++) tot += (int64_t)h_pc[p];
+    const int64_t k = std::min(tot, ids_n);
+    if (k > 0) {  // straight into the caller's array
+      HIPCHK(c, hipMemcpyAsync(o->ids, c->ids.p, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    o->n_ids = tot;
+    if (c->timed(4)) HIPCHK(c, hipEventElapsedTime(&o->ms_emit, c->ev[4], c->ev[5]));
+  }
   if (c->up_verify && h_hdr[dr::PH_UPBAD] > 0) return 2;  // an upward edge changes a cone: the general sweep
   if (c->slice_on) {
     dr_slice_out &so = c->slice_res;
@@ -4183,6 +4262,8 @@ extern "C" int dr_replay(dr_ctx *c, int nwaves, int chain_mode, int deliver_mode
   o->sweep_count = o->sweep_partial = o->sweep_row_bytes = o->sweep_weak_scanned = o->sweep_shortcut = 0;
   o->n_ids = 0;
   o->canon_segments = -1;
+  const bool want_ids = o->ids && o->ids_cap > 0;
+  if (want_ids) c->ids_form = 0;  // (1 below, when the device-planned id pass wrote them)
   if (c->general()) {
     // weak edges to the same or a later round (App. A Q8): the memo replay on the regular
     // graph, then a check that no such edge changes a cone it computed (k_verify_up)
@@ -4205,9 +4286,13 @@ extern "C" int dr_replay(dr_ctx *c, int nwaves, int chain_mode, int deliver_mode
     return general_replay(c, nwaves, chain_mode, deliver_mode, o);
   }
   c->last_path = 0;
-  if (c->plan_mode != 0 && c->memo_on() && !(o->ids && o->ids_cap > 0) && o->push_wave &&
-      o->pop_count && o->pop_digest) {
-    const int rc = replay_planned(c, nwaves, chain_mode, deliver_mode == DR_DELIVER_PAPER, o);
+  // ids: the PAPER order alone is planned on the device (DR_OPT_DEVICE_IDS); a REF pop delivers
+  // its whole history again, a stream nobody holds for a long DAG
+  const bool dev_ids = want_ids && deliver_mode == DR_DELIVER_PAPER && c->device_ids != 0;
+  if (c->plan_mode != 0 && c->memo_on() && (!want_ids || dev_ids) && o->push_wave && o->pop_count &&
+      o->pop_digest) {
+    const int rc = replay_planned(c, nwaves, chain_mode, deliver_mode == DR_DELIVER_PAPER, o, dev_ids);
+    if (rc == DR_OK && dev_ids) c->ids_form = 1;
     if (rc != 1) return rc;
   }
   // 0+1. round summaries + canonical cone, fused with the commit decisions of
@@ -4641,3 +4726,4 @@ extern "C" int dr_slice_result(const dr_ctx *c, dr_slice_out *out) {
 }
 
 extern "C" int dr_last_replay_path(const dr_ctx *c) { return c ? c->last_path : DR_E_INVAL; }
+extern "C" int dr_last_ids_form(const dr_ctx *c) { return c ? c->ids_form : -1; }

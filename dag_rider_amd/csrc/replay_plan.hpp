@@ -656,12 +656,49 @@ __global__ __launch_bounds__(NT) void k_paper_plan(int T, int dmax, const int32_
   }
 }
 
+// The set the first pop p of a query delivers at round r, word `lane` (lane < WS): the
+// base set (K_r when r <= cut, else the query's mask row at moff) & P_r, minus the base
+// sets of every candidate owner below p at r.  k_paper_emit (counts, digest, edges) and
+// k_paper_ids (the ids) both take the delivered set from here.  self: the index of the
+// query's own entry among the round's qr_list entries (r > cut: its own range), where the
+// id pass keeps the round's position; untouched at r <= cut.
+template <int WS>
+__device__ __forceinline__ u64 paper_delivered_word(const DagView &g, const u64 *__restrict__ K,
+                                                    const u64 *__restrict__ masks,
+                                                    const uint32_t *__restrict__ firstK,
+                                                    const uint32_t *__restrict__ qr_off,
+                                                    const int32_t *__restrict__ qr_list, int r, int lane, int p,
+                                                    int cut, int64_t moff, uint32_t &self) {
+  const u64 pw = g.present[(size_t)r * WS + lane];
+  const uint32_t fk = firstK[r];
+  const u64 kw = K[(size_t)r * WS + lane];
+  u64 base = r <= cut ? kw : masks[moff + (int64_t)r * WS + lane];
+  u64 ex = (int64_t)fk < (int64_t)p ? kw : 0ULL;  // K's owner comes first
+  for (uint32_t i = qr_off[r]; i < qr_off[r + 1]; i++) {
+    const int32_t *e = qr_list + 3 * (size_t)i;
+    const int64_t mo = (int64_t)(((uint64_t)(uint32_t)e[2] << 32) | (uint32_t)e[1]);
+    if (mo == moff) self = i;
+    if (e[0] < p) ex |= masks[mo + (int64_t)r * WS + lane];
+  }
+  return base & ~ex & pw;
+}
+
+// What k_paper_emit leaves for the id pass (k_paper_ids_plan, k_paper_ids) when ids are
+// requested: each query's first delivered round and, per delivered round, its exclusive
+// position within the pop -- rounds a..cut by round (those ranges are disjoint: first_K
+// there is the query's own first pop), the own rounds by their qr_list entry.
+struct PaperIds {
+  int32_t *qa;        // [query] first delivered round a
+  uint32_t *pos_k;    // [round] position of round r <= cut of the query owning K_r
+  uint32_t *pos_own;  // [qr_list entry] position of an own round
+};
+
 // One workgroup per query q (its first pop p delivers): rounds a..top, a = the
 // first round with first_K = p (merged queries whose K range starts there) or
-// lo_q.  Round r: the base set (K_r when r <= cut_q, else q's mask row) & P_r,
-// minus the base sets of every candidate owner below p at r; positions from the
-// counts of the rounds below (NT/64 rounds at a time, one per wave).
-template <int WS, int NT>
+// lo_q.  Round r: the delivered set (paper_delivered_word); positions from the
+// counts of the rounds below (NT/64 rounds at a time, one per wave).  IDS: the
+// positions are kept for the id pass (pid).
+template <int WS, int NT, bool IDS>
 __global__ __launch_bounds__(NT) void k_paper_emit(DagView g, const u64 *__restrict__ K, const u64 *__restrict__ masks,
                                                    const int32_t *__restrict__ plan, const SweepQuery *__restrict__ dq,
                                                    const int32_t *__restrict__ firstpop,
@@ -672,7 +709,7 @@ __global__ __launch_bounds__(NT) void k_paper_emit(DagView g, const u64 *__restr
                                                    const uint32_t *__restrict__ slot_off,
                                                    const uint16_t *__restrict__ slot_src,
                                                    u64 *__restrict__ qcount, u64 *__restrict__ qdigest,
-                                                   u64 *__restrict__ qedges) {
+                                                   u64 *__restrict__ qedges, const PaperIds pid) {
   constexpr int NWV = NT / 64;
   __shared__ u64 s_c[NWV], s_acc[2];
   __shared__ int s_a;
@@ -707,26 +744,15 @@ __global__ __launch_bounds__(NT) void k_paper_emit(DagView g, const u64 *__restr
   }
   __syncthreads();
   const int a = s_a;
+  if constexpr (IDS)
+    if (tid == 0) pid.qa[q] = a;
   u64 run = 0, dg = 0, ed = 0;
   for (int y0 = a; y0 <= top; y0 += NWV) {  // block-uniform
     const int r = y0 + wid;
     const bool on = r <= top;
     u64 mw = 0;
-    if (on && lane < WS) {
-      const u64 pw = g.present[(size_t)r * WS + lane];
-      const uint32_t fk = firstK[r];
-      const u64 kw = K[(size_t)r * WS + lane];
-      u64 base = r <= cut ? kw : masks[moff + (int64_t)r * WS + lane];
-      u64 ex = (int64_t)fk < (int64_t)p ? kw : 0ULL;  // K's owner comes first
-      for (uint32_t i = qr_off[r]; i < qr_off[r + 1]; i++) {
-        const int32_t *e = qr_list + 3 * (size_t)i;
-        if (e[0] < p) {
-          const int64_t mo = (int64_t)(((uint64_t)(uint32_t)e[2] << 32) | (uint32_t)e[1]);
-          ex |= masks[mo + (int64_t)r * WS + lane];
-        }
-      }
-      mw = base & ~ex & pw;
-    }
+    uint32_t self = 0;
+    if (on && lane < WS) mw = paper_delivered_word<WS>(g, K, masks, firstK, qr_off, qr_list, r, lane, p, cut, moff, self);
     const u64 cnt = wave_sum((u64)popc64(mw));
     if (lane == 0) s_c[wid] = cnt;
     __syncthreads();
@@ -737,6 +763,8 @@ __global__ __launch_bounds__(NT) void k_paper_emit(DagView g, const u64 *__restr
       pos += i < wid ? c : 0ULL;
       tot += c;
     }
+    if constexpr (IDS)
+      if (on && lane == 0) (r <= cut ? pid.pos_k[r] : pid.pos_own[self]) = (uint32_t)pos;
     if (on && cnt)  // PAPER delivers an id once, at its first slot
       dg += wave_emit_round<WS, 8, true>(slot_off, slot_src, r, mw, pos, g.sdeg, g.wdeg, g.n, &ed, g.slot_rep, g.roff);
     run += tot;
@@ -753,6 +781,140 @@ __global__ __launch_bounds__(NT) void k_paper_emit(DagView g, const u64 *__restr
     qcount[q] = run;
     qdigest[q] = s_acc[0];
     qedges[q] = s_acc[1];
+  }
+}
+
+// The id pass of the PAPER replay (DR_OPT_DEVICE_IDS), after k_paper_emit<IDS>.  One
+// workgroup plans it: qpos[q] = the global position of the first vertex query q's first
+// pop delivers (the exclusive prefix, in pop order, of the pops' delivered counts: a pop
+// delivers qcount[q] when it is its query's first, else nothing), and the work items of
+// k_paper_ids -- blocks of rpb rounds of each delivering query's range a..top:
+// item_pref[q] = the first item of query q, item_pref[nq] = their number.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_paper_ids_plan(const int32_t *__restrict__ plan,
+                                                       const int32_t *__restrict__ pop_q,
+                                                       const SweepQuery *__restrict__ dq,
+                                                       const int32_t *__restrict__ firstpop,
+                                                       const int32_t *__restrict__ qa,
+                                                       const u64 *__restrict__ qcount, int rpb,
+                                                       int64_t *__restrict__ qpos, int32_t *__restrict__ item_pref) {
+  __shared__ int64_t s[NT / 64];
+  const int tid = threadIdx.x;
+  const int caperr = plan[PL_CAPERR];
+  const int64_t np = caperr ? 0 : plan[PL_NPUSH];
+  const int nq = caperr ? 0 : plan[PL_NQD];
+  int64_t run = 0;  // block-uniform
+  for (int64_t p0 = 0; p0 < np; p0 += NT) {
+    const int64_t p = p0 + tid;
+    int q = -1;
+    if (p < np) {
+      q = pop_q[p];
+      if (firstpop[q] != (int32_t)p) q = -1;
+    }
+    const int64_t c = q >= 0 ? (int64_t)qcount[q] : 0;
+    int64_t tot;
+    const int64_t ex = block_scan_excl<NT>(c, s, tot);
+    if (q >= 0) qpos[q] = run + ex;
+    run += tot;
+  }
+  int64_t items = 0;
+  for (int q0 = 0; q0 < nq; q0 += NT) {
+    const int q = q0 + tid;
+    int64_t it = 0;
+    if (q < nq && qcount[q]) it = (dq[q].top - qa[q] + rpb) / rpb;  // rounds a..top, rpb a block
+    int64_t tot;
+    const int64_t ex = block_scan_excl<NT>(it, s, tot);
+    if (q < nq) item_pref[q] = (int32_t)(items + ex);
+    items += tot;
+  }
+  if (tid == 0) item_pref[nq] = (int32_t)items;
+}
+
+// One wave writes the ids of round y: the delivered slots (source bit set in mw, lane w
+// holding word w; a repeated id at its first slot only) in slot order, ranked as
+// wave_emit_slots ranks them, the vertex of rank k at ids[at + k] = (y + koff, source).
+// A lane's slots are adjacent, so its ids are, and a round's ids form one run.
+template <int WS, int SPL>
+__device__ __forceinline__ void wave_write_ids(const uint16_t *__restrict__ slot_src, int y, uint32_t sa, uint32_t sb,
+                                               u64 mw, int64_t at, const uint8_t *__restrict__ first_only, int koff,
+                                               int2 *__restrict__ ids, int64_t ids_cap) {
+  const int lane = threadIdx.x & 63;
+  for (uint32_t c0 = sa; c0 < sb; c0 += 64 * SPL) {
+    const uint32_t i0 = c0 + (uint32_t)lane * SPL;
+    int src[SPL];
+#pragma unroll
+    for (int j = 0; j < SPL; j++) src[j] = i0 + j < sb ? (int)slot_src[i0 + j] : 0;
+    if (first_only)
+#pragma unroll
+      for (int j = 0; j < SPL; j++)
+        if (i0 + j < sb && first_only[i0 + j]) src[j] = 0;
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < SPL; j++) {
+      const int s = src[j] - 1;
+      const u64 w = __shfl(mw, s >= 0 ? (s >> 6) & (WS - 1) : 0);
+      if (s >= 0 && ((w >> (s & 63)) & 1ULL)) bits |= 1u << j;
+    }
+    const int cnt = __popc(bits);
+    int x = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int yv = __shfl_up(x, off);
+      if (lane >= off) x += yv;
+    }
+    const int total = __shfl(x, 63);
+    int64_t k = at + (x - cnt);
+#pragma unroll
+    for (int j = 0; j < SPL; j++) {
+      if (!((bits >> j) & 1u)) continue;
+      if ((uint64_t)k < (uint64_t)ids_cap) ids[k] = make_int2(y + koff, src[j]);  // (a bad position writes nothing)
+      k++;
+    }
+    at += total;
+  }
+}
+
+// The ids of the PAPER total order.  A fixed grid strides over k_paper_ids_plan's items;
+// an item is NT/64 rounds of one query's delivered range, a wave each, so a long range
+// (a late first commit: the first pop delivers everything below it) spreads over the
+// device.  Round r: the delivered set again (paper_delivered_word), its position from
+// k_paper_emit, the ids at ids[qpos[q] + position ..] while below ids_cap.
+template <int WS, int NT>
+__global__ __launch_bounds__(NT) void k_paper_ids(DagView g, const u64 *__restrict__ K, const u64 *__restrict__ masks,
+                                                  const int32_t *__restrict__ plan, const SweepQuery *__restrict__ dq,
+                                                  const int32_t *__restrict__ firstpop,
+                                                  const int32_t *__restrict__ qcut,
+                                                  const uint32_t *__restrict__ firstK,
+                                                  const uint32_t *__restrict__ qr_off,
+                                                  const int32_t *__restrict__ qr_list,
+                                                  const uint32_t *__restrict__ slot_off,
+                                                  const uint16_t *__restrict__ slot_src, const PaperIds pid,
+                                                  const int64_t *__restrict__ qpos,
+                                                  const int32_t *__restrict__ item_pref, int2 *__restrict__ ids,
+                                                  int64_t ids_cap) {
+  constexpr int RPB = NT / 64;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (plan[PL_CAPERR]) return;
+  const int nq = plan[PL_NQD];
+  const int nit = item_pref[nq];
+  for (int it = blockIdx.x; it < nit; it += gridDim.x) {  // (no barrier inside: waves run free)
+    int q = 0, h = nq;  // the last query whose first item is <= it (queries without items share a prefix)
+    while (h - q > 1) {
+      const int m = (q + h) >> 1;
+      if (item_pref[m] <= it) q = m; else h = m;
+    }
+    const int top = dq[q].top;
+    const int r = pid.qa[q] + (it - item_pref[q]) * RPB + wid;
+    if (r > top) continue;  // wave-uniform
+    const int p = firstpop[q], cut = qcut[q];
+    const int64_t moff = dq[q].mask_off;
+    u64 mw = 0;
+    uint32_t self = 0;
+    if (lane < WS) mw = paper_delivered_word<WS>(g, K, masks, firstK, qr_off, qr_list, r, lane, p, cut, moff, self);
+    if (__ballot(mw != 0) == 0) continue;  // wave-uniform: the round delivers nothing
+    self = __shfl(self, 0);
+    const int64_t at = qpos[q] + (int64_t)(r <= cut ? pid.pos_k[r] : pid.pos_own[self]);
+    wave_write_ids<WS, 16>(slot_src, r, slot_off[r], slot_off[r + 1], mw, at, g.slot_rep, g.roff, ids, ids_cap);
   }
 }
 

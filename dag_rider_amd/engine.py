@@ -97,6 +97,16 @@ class Engine:
         """DR_OPT_DEVICE_PLAN: plan dr_replay's phases on the device (identical results either way)."""
         self._check(self._L.dr_set_option(self._h, L.DR_OPT_DEVICE_PLAN, int(on)))
 
+    def set_device_ids(self, on: bool):
+        """DR_OPT_DEVICE_IDS: a PAPER replay that requests ids stays device-planned (the id pass
+        writes the total order on the device; identical results either way)."""
+        self._check(self._L.dr_set_option(self._h, L.DR_OPT_DEVICE_IDS, int(on)))
+
+    def last_ids_form(self) -> int:
+        """dr_last_ids_form: how the last replay that requested ids produced them -- 1 the
+        device-planned id pass, 0 host-planned, -1 none requested yet."""
+        return int(self._L.dr_last_ids_form(self._h))
+
     def set_commit_split(self, mode: int):
         """DR_OPT_COMMIT_SPLIT: several workgroups per wave for short wave ranges (1: every range
         shorter than the CU count, 2: ranges of at most 4 waves, the default; 0 = one workgroup

@@ -48,6 +48,8 @@ const (
 	LeaderConst1    = int(C.DR_LEADER_CONST1) // chooseLeader as written: process 1
 	LeaderSeeded    = int(C.DR_LEADER_SEEDED)
 	LeaderTable     = int(C.DR_LEADER_TABLE)
+	// dr_set_option: a PAPER Replay that requests ids stays device-planned (default 1)
+	OptDeviceIDs = int(C.DR_OPT_DEVICE_IDS)
 )
 
 // Mirror is one device copy of a Process's DAG (one dr_ctx).
@@ -215,6 +217,11 @@ func (m *Mirror) WaveLeader(wave int) int { return int(C.dr_wave_leader(m.ctx, C
 // captured hipGraph was launched (DR_OPT_REPLAY_GRAPH), 0 = kernel by kernel, -1 = kernel by
 // kernel after a failed capture.
 func (m *Mirror) ReplayGraphState() int { return int(C.dr_replay_graph_state(m.ctx)) }
+
+// LastIdsForm is how the mirror's last Replay that requested ids produced them
+// (dr_last_ids_form): 1 = the device-planned id pass (DR_OPT_DEVICE_IDS), 0 = the
+// host-planned replay, -1 = none requested ids yet.
+func (m *Mirror) LastIdsForm() int { return int(C.dr_last_ids_form(m.ctx)) }
 
 // WaveReady is waveReady(wave) (process.go:314-354) given decidedWave: the
 // commit decision, the vote count (-1: no leader vertex) and on commit the

@@ -49,7 +49,7 @@ enum {
 };
 enum { DR_CHAIN_LITERAL = 0, DR_CHAIN_PERSISTENT = 1 };
 enum { DR_OPT_MEMO = 1, DR_OPT_DEVICE_PLAN = 2, DR_OPT_PHASE_TIMING = 3, DR_OPT_BATCH_FORM = 4, DR_OPT_COMMIT_SPLIT = 5,
-       DR_OPT_REPLAY_GRAPH = 6, DR_OPT_FUSE = 7, DR_OPT_CALL_OVERLAP = 8 };
+       DR_OPT_REPLAY_GRAPH = 6, DR_OPT_FUSE = 7, DR_OPT_CALL_OVERLAP = 8, DR_OPT_DEVICE_IDS = 9 };
 enum { DR_BATCH_AUTO = 0, DR_BATCH_WORKGROUP = 1, DR_BATCH_WAVE = 2 };
 enum { DR_DELIVER_REF = 0, DR_DELIVER_PAPER = 1 };
 enum { DR_WEAK_LITERAL = 0, DR_WEAK_PAPER = 1 };
@@ -103,7 +103,7 @@ int dr_wave_leader(const dr_ctx *ctx, int wave);
  * 1023 rounds.
  * DR_OPT_DEVICE_PLAN (default 1): dr_replay plans its chain, pop and emission
  * phases on the device (one host synchronisation per replay) when summaries
- * are on and no ids are requested, in both delivery modes; 0 = plan on the
+ * are on and no ids are requested (PAPER ids too: DR_OPT_DEVICE_IDS), in both delivery modes; 0 = plan on the
  * host between phases (identical results).
  * DR_OPT_PHASE_TIMING (default 2): HIP events time every phase of a
  * device-planned dr_replay (ms_* outputs); 1 = the summary pass only, 0 = none
@@ -137,7 +137,15 @@ int dr_wave_leader(const dr_ctx *ctx, int wave);
  * the next REF dr_order_vertices merges with) without waiting for it: 1 = behind the
  * commit rule on the context's stream when no leader chain can follow (decided_wave >=
  * wave - 1), else after the wave's commit is known; 2 = on a second stream beside the
- * commit rule; 0 = dr_order_vertices computes it.  Identical results. */
+ * commit rule; 0 = dr_order_vertices computes it.  Identical results.
+ * DR_OPT_DEVICE_IDS (default 1): a DR_DELIVER_PAPER dr_replay that requests ids (ids set,
+ * ids_cap > 0) stays device-planned when DR_OPT_DEVICE_PLAN applies: an id pass after the
+ * planned replay writes the total order -- every vertex once, in a_deliver order -- on the
+ * device, and min(n_ids, ids_cap) ids come back in one copy.  Such a replay launches kernel
+ * by kernel even with DR_OPT_REPLAY_GRAPH 1 (dr_replay_graph_state: 0), and with
+ * DR_OPT_PHASE_TIMING 2 ms_emit is the id pass's device time.  0 = the host-planned replay,
+ * as for DR_DELIVER_REF ids (a REF pop delivers its whole history again: no bounded
+ * stream).  Identical results. */
 int dr_set_option(dr_ctx *ctx, int option, int value);
 /* The form of the context's last dr_replay: 1 = a captured graph was launched,
  * 0 = kernels launched one by one, -1 = one by one after a failed capture
@@ -397,6 +405,10 @@ int dr_last_append_phases(const dr_ctx *ctx, float *ms4);
  * general sweep (strong edges upward, too many such edges, or PAPER delivery); -1
  * none yet. */
 int dr_last_replay_path(const dr_ctx *ctx);
+/* How the last dr_replay that requested ids produced them: 1 = the device-planned id pass
+ * (DR_OPT_DEVICE_IDS) wrote them, 0 = the host-planned replay, -1 = no dr_replay of this
+ * context requested ids yet.  A replay without ids leaves the value as it was. */
+int dr_last_ids_form(const dr_ctx *ctx);
 
 /* Wave-range slice of one DAG (SURVEY.md s8(e) row 1 widened to the whole replay:
  * waveReady :314-354 and orderVertices :404-443 of a contiguous wave range on the GPU
